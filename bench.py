@@ -508,6 +508,29 @@ def reference_benchmark_rows(sv, dev, cpu_legs=True):
     return out, ok
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out, directory, seed=0):
+    """Writes the arrays the timed step returned (dict name -> tensor) as <directory>/<name>.npy: float64 tensors as float64, other
+    floats as float32, integers as float64 (exact up to 2^53).  Together at most DUMP_BYTES; an array over its share of that is
+    replaced by <name>_sample.npy, its elements at a fixed seeded set of flat indices (sorted), so that two runs compare element for
+    element."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: v for k, v in sorted(out.items()) if torch.is_tensor(v)}
+    share = DUMP_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        dtype = torch.float64 if t.dtype == torch.float64 or not t.dtype.is_floating_point else torch.float32
+        flat = t.detach().reshape(-1)
+        n_max = share // (8 if dtype == torch.float64 else 4)
+        if flat.numel() > n_max:
+            idx = np.unique(np.random.default_rng(seed).integers(0, flat.numel(), n_max))
+            flat, name = flat[torch.from_numpy(idx).to(flat.device)], name + "_sample"
+        else:
+            flat = flat.reshape(t.shape)
+        np.save(os.path.join(directory, name + ".npy"), flat.to(dtype).cpu().numpy())
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -546,8 +569,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=7, help="the K-step timed region is run this many times (each bracketed by barrier + synchronize, "
-                    "max over ranks); ms_per_step / value are the MEDIAN region, min and max are in the line (K = 20 is a 1.7 ms window)")
+    ap.add_argument("--repeats", type=int, default=1, help="the K-step timed region is run this many times (each bracketed by barrier + synchronize, "
+                    "max over ranks); ms_per_step / value are the MEDIAN region, min and max are in the line (K = 20 is a 1.7 ms window).  "
+                    "The default, one region, makes --steps the number of timed steps")
     ap.add_argument("--no-configs", action="store_true", help="N = 1: skip the other BASELINE configurations (C1, C2, C4, one-GPU C5) after the headline")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU oracle legs (cpu_baseline and end_px_err)")
     ap.add_argument("--no-api-chain", action="store_true", help="skip the per-function (volume-materialising) chain")
@@ -562,6 +586,9 @@ def main():
     ap.add_argument("--two-frames", action="store_true", help="after the timed region, also time consecutive frames alternating between two "
                     "HIP streams (information only; kept out of the default run so that a profiler's per-kernel averages of this command "
                     "describe the single-stream kernels)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one returned (rank 0) to DIR/<name>.npy "
+                    "(float32 / float64, at most 64 MB in all: a fixed seeded sample of a larger array); the inputs are seeded, so two builds "
+                    "can be compared output for output")
     args = ap.parse_args()
 
     if needs_launch(args.gpus, os.environ):
@@ -689,6 +716,8 @@ def main():
     elapsed = float(np.median(regions))
     disp_dev = out["disp"]
     checksum = int(disp_dev.sum().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
 
     # ---- N > 1: the phases of one frame, un-overlapped, outside the timed region (events on the compute stream; the exchange is
     # bracketed with the compute stream waiting for RCCL's stream, so its figure is what a non-pipelined frame would pay)

@@ -53,3 +53,27 @@ def test_mismatched_world_size_is_refused():
     env = dict(os.environ, WORLD_SIZE="4", RANK="0", LOCAL_RANK="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], capture_output=True, text=True, env=env, timeout=300)
     assert p.returncode != 0 and "--gpus 2 but WORLD_SIZE=4" in p.stderr
+
+
+def test_dump_outputs_types_budget_and_fixed_sample(tmp_path):
+    """--dump-outputs: integers and float64 as float64, other floats as float32, at most 64 MB in all; an array over its share is a
+    seeded sample, the same sample on every run."""
+    import numpy as np
+    import torch
+
+    import bench
+    bench.torch = torch
+    disp = torch.arange(1080 * 1920, dtype=torch.int32).reshape(1080, 1920)
+    refined = torch.full((4, 5), 0.5, dtype=torch.float16)
+    big = torch.arange(20_000_000, dtype=torch.float64)
+    for d in ("a", "b"):
+        bench.dump_outputs({"disp": disp, "refined": refined, "cv": big, "none": None}, str(tmp_path / d))
+    assert sorted(os.listdir(tmp_path / "a")) == ["cv_sample.npy", "disp.npy", "refined.npy"]
+    got = np.load(tmp_path / "a" / "disp.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, disp.numpy())
+    got = np.load(tmp_path / "a" / "refined.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, np.full((4, 5), 0.5, np.float32))
+    s = np.load(tmp_path / "a" / "cv_sample.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, np.load(tmp_path / "b" / "cv_sample.npy"))
+    assert np.all(np.diff(s) > 0) and s[-1] < big.numel()  # distinct elements of the array, in index order
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_BYTES + 1024

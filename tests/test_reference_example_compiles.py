@@ -1,9 +1,10 @@
 """north_star: "keeping the StereoVision::Correlation template/API surface so it drops into examples/stereo-match unchanged".
 
-The reference's own examples/stereo-match/main.cpp -- READ FROM /root/reference AT TEST TIME, never copied into this repository and never
-sent to the GPU box (the tests skip where that tree is absent) -- compiles with `-I libstevi_amd/include` first on the include path and
-links against libstevi_hip.so.  The only file the test supplies besides the product headers is tests/cpp/tclap/CmdLine.h, a tests-only
-subset of TCLAP (the image has no TCLAP; it is argument parsing, not part of the path).  WITH_GUI is not defined (Qt display code).
+The reference's own examples/stereo-match/main.cpp -- read in place by build() (oracle/Makefile, target `ref`), never copied into this
+repository -- compiles with `-I libstevi_amd/include` first on the include path and links against libstevi_hip.so, into
+oracle/_ref/stereo_match; oracle/_ref/stereo_match.d lists the headers the compile read (the tests skip where build() found no reference
+tree).  The only file the build supplies besides the product headers is tests/cpp/tclap/CmdLine.h, a tests-only subset of TCLAP (the
+image has no TCLAP; it is argument parsing, not part of the path).  WITH_GUI is not defined (Qt display code).
 
 What the translation unit takes from the shim tree (main.cpp:21-31, :150-210): io/image_io.h::readImage, MatchingFunctionTraits<ZNCC>,
 OnDemandDecoratedFeaturesVolume<ZNFeaturesVolumeDecorator<...>>, searchOffset<2>, cachelessPatchMatch<ZNCC, 2>,
@@ -20,31 +21,26 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFERENCE_MAIN = "/root/reference/examples/stereo-match/main.cpp"
+EXE = os.path.join(ROOT, "oracle", "_ref", "stereo_match")
 
-pytestmark = pytest.mark.skipif(not os.path.exists(REFERENCE_MAIN), reason="the reference tree is not on this machine")
+pytestmark = pytest.mark.skipif(not os.path.exists(EXE), reason="oracle/_ref/stereo_match was not built: build() found no reference tree")
 
 
 @pytest.fixture(scope="module")
-def stereo_match(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("stereo_match") / "stereo_match")
-    # the shim directory FIRST, then the tests-only TCLAP subset; nothing from /root/reference is on the include path
-    cmd = ["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "libstevi_amd", "include"), "-I", os.path.join(ROOT, "tests", "cpp"),
-           REFERENCE_MAIN, "-o", exe, "-L", os.path.join(ROOT, "libstevi_amd"), "-lstevi_hip", "-Wl,-rpath," + os.path.join(ROOT, "libstevi_amd"),
-           "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64", "-lpthread"]
-    out = subprocess.run(cmd, capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-4000:]
-    return exe
+def stereo_match():
+    return EXE
 
 
 def test_reference_stereo_match_main_compiles_and_links_unchanged(stereo_match):
-    assert os.path.exists(stereo_match)
+    assert os.access(stereo_match, os.X_OK)
     # the translation unit is the reference's, byte for byte: nothing was preprocessed in or patched (the compile read it in place)
-    deps = subprocess.run(["g++", "-std=c++17", "-MM", "-I", os.path.join(ROOT, "libstevi_amd", "include"), "-I", os.path.join(ROOT, "tests", "cpp"),
-                           REFERENCE_MAIN], capture_output=True, text=True)
-    assert deps.returncode == 0
-    headers = [os.path.normpath(t) for t in deps.stdout.replace("\\\n", " ").split() if t.endswith(".h")]
-    assert headers and not [h for h in headers if h.startswith("/root/reference")], "a header came from the reference tree"
+    with open(stereo_match + ".d") as f:
+        deps = f.read().replace("\\\n", " ").split()[1:]
+    mains = [d for d in deps if d.endswith("examples/stereo-match/main.cpp")]
+    assert len(mains) == 1, deps[:4]
+    reference = os.path.normpath(os.path.join(os.path.dirname(mains[0]), "..", ".."))
+    headers = [os.path.normpath(t) for t in deps if t.endswith(".h")]
+    assert headers and not [h for h in headers if h.startswith(reference + os.sep)], "a header came from the reference tree"
     for needed in ("correlation/patchmatch.h", "correlation/hierarchical.h", "correlation/image_based_refinement.h", "correlation/on_demand_features_volume.h",
                    "correlation/on_demand_cost_volume.h", "correlation/cost_based_refinement.h", "utils/contiguity.h", "io/image_io.h"):
         assert any(h.endswith("libstevi_amd/include/" + needed) for h in headers), needed
@@ -68,7 +64,7 @@ def test_reference_stereo_match_argument_handling_and_image_loading(stereo_match
 
 def test_reference_stereo_match_has_no_cpu_fallback(stereo_match):
     """On a machine without a HIP device the example loads its images through the shim's readImage and then fails loudly at the first
-    compute call; with a device (the GPU box never has the reference tree, so this only runs on a developer's GPU machine) it finishes."""
+    compute call; with a device (where oracle/_ref/stereo_match was built on, or brought to, a GPU machine) it finishes."""
     import libstevi_amd._capi as capi
     pair = os.path.join(ROOT, "tests", "golden", "stereo_pair")
     out = subprocess.run([stereo_match, os.path.join(pair, "img_r.stevimg"), os.path.join(pair, "img_l.stevimg"), "--right-search-delta=8", "--n-iter=3", "--refine"],
