@@ -59,6 +59,7 @@ typedef enum svh_dtype { SVH_F32 = 0, SVH_I32 = 1, SVH_U32 = 2, SVH_U8 = 3, SVH_
 /* values of StereoVision::Correlation::matchingFunctions, correlation/matching_costs.h:38-53 */
 typedef enum svh_match_func {
     SVH_CC = 0, SVH_NCC = 1, SVH_SSD = 2, SVH_SAD = 3, SVH_ZCC = 4, SVH_ZNCC = 5, SVH_ZSSD = 6, SVH_ZSAD = 7,
+    SVH_MEDAD = 8, SVH_ZMEDAD = 9, /* cost-volume entry points and svh_stereo_match only (see svh_feature_cost_volume) */
     SVH_HAMMING = 10, SVH_CENSUS = 11
 } svh_match_func;
 

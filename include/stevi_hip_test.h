@@ -35,6 +35,9 @@ extern "C" {
  * reference's compressors, 3x3 / 5x5 unfolds) are compared with the TARGET record in registers -- a lane owns a record and walks the source
  * pixels that look at it, two at a time with packed multiplies and adds; 0: every target feature of every voxel is read from LDS (round 4).
  * Same bits.
+ * "median_form" (default 0): MEDAD / ZMEDAD cost volumes -- 0 the selection network for F in {9, 25, 27, 49, 75, 81} and the bitwise
+ * selection over the 31 key bits from LDS for every other F; 1 the bitwise selection from LDS for every F; 2 a thread per voxel with the
+ * bitwise selection from global memory (what vectors too long for LDS take).  Same bits.
  * "extract_index_wide" (default 1): svh_extract_selected_index (and every call that picks winners from a float volume) on rows of up to
  * 1 024 costs the packed kernel does not take -- more than 256 costs, or a count that is no multiple of four (2-D volumes: 289, 297) --
  * keeps up to sixteen costs per lane and combines by two all-reduces per pixel; 0: the wave-per-pixel kernel of round 1.  Same result.

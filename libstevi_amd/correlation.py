@@ -25,6 +25,8 @@ class matchingFunctions(enum.IntEnum):  # correlation/matching_costs.h:38-53
     ZNCC = 5
     ZSSD = 6
     ZSAD = 7
+    MEDAD = 8   # median absolute difference: cost volumes and stereoMatch (not computeGuidedCV / hierarchical / PatchMatch / on-demand)
+    ZMEDAD = 9  # its zero-mean form (same scope)
     HAMMING = 10
     CENSUS = 11
 

@@ -20,6 +20,10 @@ int fail(svh_context *ctx, int status, const char *fmt, ...) {
     return status;
 }
 
+int func_refusal(svh_context *ctx, int f, const char *where) {
+    return fail(ctx, SVH_ERR_UNSUPPORTED, "matching function %d (%s) is not available in %s", f, func_name(f), where);
+}
+
 // ---- pool ------------------------------------------------------------------------------------------
 Scratch::~Scratch() {
     for (size_t k : taken) ctx->pool[k].in_use = false;
@@ -472,6 +476,11 @@ int svh_test_set_option(svh_context *ctx, const char *name, int value) {
     if (strcmp(name, "guided_shared") == 0) {
         if (value < 0 || value > 3) return fail(ctx, SVH_ERR_INVALID_ARGUMENT, "guided_shared: 0 .. 3");
         ctx->guided_shared = value;
+        return SVH_OK;
+    }
+    if (strcmp(name, "median_form") == 0) {
+        if (value < 0 || value > 2) return fail(ctx, SVH_ERR_INVALID_ARGUMENT, "median_form: 0 .. 2");
+        ctx->median_form = value;
         return SVH_OK;
     }
     if (strcmp(name, "patchmatch_search_form") == 0) {

@@ -587,6 +587,7 @@ int dev_hamming_volume(svh_context *ctx, const CostVolumeArgs &a, const uint32_t
 
 int dev_cost_volume_from_features(svh_context *ctx, Scratch &scr, const CostVolumeArgs &a, const float *feat_src,
                                   const float *feat_tgt, int F, float *cv) {
+    if (func_median(a.func)) return dev_median_volume_from_features(ctx, scr, a, feat_src, feat_tgt, F, cv); // (a selection: nothing here applies)
     if (func_census(a.func)) {
         int nWw = census_words_written(F);
         uint32_t *sw = scr.get_n<uint32_t>((size_t)a.H * a.Ws * (nWw ? nWw : 1));
@@ -603,6 +604,7 @@ int dev_cost_volume_from_features(svh_context *ctx, Scratch &scr, const CostVolu
 
 int dev_cost_volume_from_images(svh_context *ctx, Scratch &scr, const CostVolumeArgs &a, ImageDesc src, ImageDesc tgt, int h_r,
                                 int v_r, float *cv) {
+    if (func_median(a.func)) return dev_median_volume_from_images(ctx, scr, a, src, tgt, h_r, v_r, cv); // (no column sums, no reduction)
     if (func_census(a.func)) {
         int F = (2 * h_r + 1) * (2 * v_r + 1) * src.C;
         int nWw = census_words_written(F);
@@ -662,7 +664,7 @@ int svh_feature_cost_volume(svh_context *ctx, int match_func, int disp_direction
     SVH_TRY(validate(ctx, feat_l, "feat_l", SVH_F32, 3, 3));
     SVH_TRY(validate(ctx, feat_r, "feat_r", SVH_F32, 3, 3));
     SVH_TRY(validate(ctx, cv, "cv", SVH_F32, 3, 3));
-    if (!func_supported(match_func)) return fail(ctx, SVH_ERR_UNSUPPORTED, "matching function %d", match_func);
+    if (!func_volume_supported(match_func)) return fail(ctx, SVH_ERR_UNSUPPORTED, "matching function %d", match_func);
     if (disp_direction != SVH_LEFT_TO_RIGHT && disp_direction != SVH_RIGHT_TO_LEFT)
         return fail(ctx, SVH_ERR_INVALID_ARGUMENT, "bad disparity direction");
     // aggregateCost: cross_correlations.h:209-211
@@ -697,7 +699,7 @@ static int unfold_cost_volume_impl(svh_context *ctx, int match_func, int disp_di
     SVH_TRY(validate_image(ctx, img_l, "img_l", match_func));
     SVH_TRY(validate_image(ctx, img_r, "img_r", match_func));
     SVH_TRY(validate(ctx, cv, "cv", SVH_F32, 3, 3));
-    if (!func_supported(match_func)) return fail(ctx, SVH_ERR_UNSUPPORTED, "matching function %d", match_func);
+    if (!func_volume_supported(match_func)) return fail(ctx, SVH_ERR_UNSUPPORTED, "matching function %d", match_func);
     if (disp_direction != SVH_LEFT_TO_RIGHT && disp_direction != SVH_RIGHT_TO_LEFT)
         return fail(ctx, SVH_ERR_INVALID_ARGUMENT, "bad disparity direction");
     if (h_radius < 0 || v_radius < 0 || h_radius > 255 || v_radius > 255)
@@ -806,7 +808,7 @@ extern "C" int svh_unfold_cost_volume_2d(svh_context *ctx, int match_func, int d
     SVH_TRY(validate_image(ctx, img_l, "img_l", match_func));
     SVH_TRY(validate_image(ctx, img_r, "img_r", match_func));
     SVH_TRY(validate(ctx, cv, "cv", SVH_F32, 4, 4));
-    if (!func_supported(match_func)) return fail(ctx, SVH_ERR_UNSUPPORTED, "matching function %d", match_func);
+    if (!func_volume_supported(match_func)) return fail(ctx, SVH_ERR_UNSUPPORTED, "matching function %d", match_func);
     if (disp_direction != SVH_LEFT_TO_RIGHT && disp_direction != SVH_RIGHT_TO_LEFT)
         return fail(ctx, SVH_ERR_INVALID_ARGUMENT, "bad disparity direction");
     if (h_radius < 0 || v_radius < 0 || h_radius > 255 || v_radius > 255)
@@ -886,7 +888,7 @@ extern "C" int svh_feature_cost_volume_2d(svh_context *ctx, int match_func, int 
     SVH_TRY(validate(ctx, feat_l, "feat_l", SVH_F32, 3, 3));
     SVH_TRY(validate(ctx, feat_r, "feat_r", SVH_F32, 3, 3));
     SVH_TRY(validate(ctx, cv, "cv", SVH_F32, 4, 4));
-    if (!func_supported(match_func)) return fail(ctx, SVH_ERR_UNSUPPORTED, "matching function %d", match_func);
+    if (!func_volume_supported(match_func)) return fail(ctx, SVH_ERR_UNSUPPORTED, "matching function %d", match_func);
     if (disp_direction != SVH_LEFT_TO_RIGHT && disp_direction != SVH_RIGHT_TO_LEFT)
         return fail(ctx, SVH_ERR_INVALID_ARGUMENT, "bad disparity direction");
     if (feat_l->shape[0] != feat_r->shape[0]) return fail(ctx, SVH_EMPTY_RESULT, "row counts differ");

@@ -5,14 +5,14 @@
 namespace svh {
 
 bool cost_volume_colsum_applies(const svh_context *ctx, const CostVolumeArgs &a, ImageDesc src, ImageDesc tgt, int h_r, int v_r) {
-    if (a.literal || src.C != tgt.C || src.C < 1 || src.C > 4 || h_r < 1 || h_r > 7 || func_census(a.func) || a.func == SVH_ZSAD || !ctx->cost_volume_colsum) return false;
+    if (a.literal || func_median(a.func) || src.C != tgt.C || src.C < 1 || src.C > 4 || h_r < 1 || h_r > 7 || func_census(a.func) || a.func == SVH_ZSAD || !ctx->cost_volume_colsum) return false;
     return colsum_shmem(v_r, a.D, func_zero_mean(a.func), func_normalized(a.func), a.n_dh, src.C) <= 78 * 1024 && (int64_t)a.H * a.Ws * a.D > 0;
 }
 
 // Returns SVH_OK when the tiled kernel ran, SVH_ERR_UNSUPPORTED (without touching the context error) when the caller must
 // use the generic kernel (multi-channel images, windows wider than 11, tiles beyond the LDS budget).
 int dev_cost_volume_grey_tiled(svh_context *ctx, Scratch &scr, const CostVolumeArgs &a_in, ImageDesc src, ImageDesc tgt, int h_r, int v_r, float *cv) {
-    if (h_r < 1 || h_r > 7 || func_census(a_in.func)) return SVH_ERR_UNSUPPORTED;
+    if (h_r < 1 || h_r > 7 || func_census(a_in.func) || func_median(a_in.func)) return SVH_ERR_UNSUPPORTED;
     CostVolumeArgs a = a_in; // (+ the channel count: colour images take the column-sum kernel with the channels as rows, or nothing here)
     a.C = src.C;
     if (src.C != 1 || tgt.C != 1 || (h_r > 5 && a.func != SVH_ZSAD)) { // (colour images, windows 13 or 15 wide: the column-sum kernel or nothing here; ZSAD on grey images: the per-window kernel)

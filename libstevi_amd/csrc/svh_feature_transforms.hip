@@ -156,7 +156,7 @@ int svh_zeromean_normalized_feature_volume(svh_context *ctx, const svh_array *fe
 int svh_feature_volume_for_match_func(svh_context *ctx, int match_func, const svh_array *feat, svh_array *out) {
     if (!ctx) return SVH_ERR_INVALID_ARGUMENT;
     SVH_TRY(validate(ctx, feat, "feat", SVH_F32, 3, 3));
-    if (!func_supported(match_func)) return fail(ctx, SVH_ERR_UNSUPPORTED, "matching function %d", match_func);
+    if (!func_volume_supported(match_func)) return fail(ctx, SVH_ERR_UNSUPPORTED, "matching function %d", match_func); // (MEDAD: a copy, ZMEDAD: zero-mean)
     const int H = (int)feat->shape[0], W = (int)feat->shape[1], F = (int)feat->shape[2];
     const int64_t npx = (int64_t)H * W;
     const bool census = func_census(match_func);

@@ -543,7 +543,7 @@ static int check_guided_outputs(svh_context *ctx, int H, int Ws, int radius, con
 extern "C" int svh_guided_cost_volume(svh_context *ctx, int match_func, int disp_direction, const svh_array *feat_l, const svh_array *feat_r,
                                       const svh_array *guide, int32_t upscale_disp_radius, svh_array *tcv, svh_array *disp) {
     if (!ctx) return SVH_ERR_INVALID_ARGUMENT;
-    if (!func_supported(match_func)) return fail(ctx, SVH_ERR_UNSUPPORTED, "matching function %d", match_func);
+    if (!func_supported(match_func)) return func_refusal(ctx, match_func, "hierarchical matching");
     const int ft = func_census(match_func) ? SVH_U32 : SVH_F32; // FeatureType, matching_costs.h:742-788
     SVH_TRY(validate(ctx, feat_l, "feat_l", ft, 3, 3));
     SVH_TRY(validate(ctx, feat_r, "feat_r", ft, 3, 3));
@@ -585,7 +585,7 @@ extern "C" int svh_hierarchical_truncated_cost_volume(svh_context *ctx, int matc
     if (!ctx) return SVH_ERR_INVALID_ARGUMENT;
     SVH_TRY(validate(ctx, img_l, "img_l", SVH_F32, 2, 3));
     SVH_TRY(validate(ctx, img_r, "img_r", SVH_F32, 2, 3));
-    if (!func_supported(match_func)) return fail(ctx, SVH_ERR_UNSUPPORTED, "matching function %d", match_func);
+    if (!func_supported(match_func)) return func_refusal(ctx, match_func, "hierarchical matching");
     if (disp_direction != SVH_LEFT_TO_RIGHT && disp_direction != SVH_RIGHT_TO_LEFT) return fail(ctx, SVH_ERR_INVALID_ARGUMENT, "bad disparity direction");
     if (depth < 1 || depth > 16) return fail(ctx, SVH_ERR_INVALID_ARGUMENT, "depth must be in [1,16] (static_assert depth > 0, hierarchical.h:243)");
     if (!h_radii || !v_radii) return fail(ctx, SVH_ERR_INVALID_ARGUMENT, "radii arrays must hold depth + 1 entries");

@@ -66,6 +66,7 @@ struct svh_context {
     bool patchmatch_run_batches = true; // svh_test_set_option("patchmatch_run_batches"): a PatchMatch sweep step that evaluates a cost on the spot evaluates the next eight pixels of its line against the same travelling candidate with it (0: one evaluation per step)
     bool patchmatch_lookback = true; // svh_test_set_option("patchmatch_lookback"): after the first iteration PatchMatch's pre-pass also evaluates every pixel against the pre-sweep solutions two to four steps back, so that a travelling candidate needs no evaluation on the spot before its fourth accepted step (0: one step back only)
     bool patchmatch_scan_chunks = true; // svh_test_set_option("patchmatch_scan_chunks"): from the second iteration on a sweep line decides 64 steps at a time by a prefix scan over per-pixel transition tables (0: step by step)
+    int median_form = 0;               // svh_test_set_option("median_form"): MEDAD / ZMEDAD volumes -- 0 the selection network where F has one, else the bitwise selection from LDS; 1 the bitwise selection from LDS always; 2 a thread per voxel from global memory
     bool literal_cost_volumes = false; // svh_context_set_option("literal_cost_volumes"): hierarchical matching uses the per-voxel kernel
     bool cost_reduce_fused = true;     // svh_test_set_option("cost_reduce_fused"): svh_stereo_match lets the float cost kernel reduce over the disparity axis while it holds the costs -- the winner of a call without SGM (no volume written), the regional minima of a Cost-branch SGM (no probing read) -- 0: separate kernels read the volume back
     bool sgm_cost_two_minima = true;   // svh_test_set_option("sgm_cost_two_minima"): the Cost branch on a float volume runs its line recurrences on the two regional minima of every pixel (one read of the volume) instead of sweeping the volume once per pass
@@ -202,7 +203,17 @@ inline int grid_for(int64_t n, int block, int max_blocks = 1 << 20) {
 
 // ---- trait helpers (correlation/matching_costs.h:419-685) -----------------------------------------
 inline bool func_supported(int f) { return (f >= SVH_CC && f <= SVH_ZSAD) || f == SVH_HAMMING || f == SVH_CENSUS; }
-inline bool func_zero_mean(int f) { return f == SVH_ZCC || f == SVH_ZNCC || f == SVH_ZSSD || f == SVH_ZSAD; }
+// MEDAD / ZMEDAD (median absolute difference, svh_cost_volume_median.hip): whole cost volumes only -- svh_feature_cost_volume(_2d),
+// svh_unfold_cost_volume(_minima, _winner, _2d), svh_stereo_match without shards, svh_feature_volume_for_match_func.  Every other entry
+// point (hierarchical matching, PatchMatch, on-demand volumes, shards) keeps func_supported and refuses them (func_refusal names them).
+inline bool func_median(int f) { return f == SVH_MEDAD || f == SVH_ZMEDAD; }
+inline bool func_volume_supported(int f) { return func_supported(f) || func_median(f); }
+inline const char *func_name(int f) {
+    static const char *names[] = {"CC", "NCC", "SSD", "SAD", "ZCC", "ZNCC", "ZSSD", "ZSAD", "MEDAD", "ZMEDAD", "HAMMING", "CENSUS", "KERMI"};
+    return f >= 0 && f <= 12 ? names[f] : "unknown";
+}
+int func_refusal(svh_context *ctx, int f, const char *where); // SVH_ERR_UNSUPPORTED, "matching function %d (%s) is not available in <where>"
+inline bool func_zero_mean(int f) { return f == SVH_ZCC || f == SVH_ZNCC || f == SVH_ZSSD || f == SVH_ZSAD || f == SVH_ZMEDAD; }
 inline bool func_normalized(int f) { return f == SVH_NCC || f == SVH_ZNCC; }
 inline bool func_census(int f) { return f == SVH_HAMMING || f == SVH_CENSUS; }
 inline int func_strategy(int f) { return (f == SVH_CC || f == SVH_NCC || f == SVH_ZCC || f == SVH_ZNCC) ? SVH_SCORE : SVH_COST; }
@@ -295,6 +306,11 @@ bool cost_volume_colsum_applies(const svh_context *ctx, const CostVolumeArgs &a,
 // Hamming volume from compact census words (src exact, tgt already rounded through float)
 int dev_hamming_volume(svh_context *ctx, const CostVolumeArgs &a, const uint32_t *src_words, const uint32_t *tgt_words, int nWw,
                        float *cv);
+// MEDAD / ZMEDAD volumes (svh_cost_volume_median.hip): always written, never reduced (a.reduce is left undone), one vertical offset per call
+int dev_median_volume_from_features(svh_context *ctx, Scratch &scr, const CostVolumeArgs &a, const float *feat_src, const float *feat_tgt, int F,
+                                    float *cv);
+int dev_median_volume_from_images(svh_context *ctx, Scratch &scr, const CostVolumeArgs &a, ImageDesc src, ImageDesc tgt, int h_r, int v_r,
+                                  float *cv);
 
 // SGM
 struct SgmArgs {

@@ -1580,7 +1580,7 @@ int check_params(svh_context *ctx, const svh_on_demand_params *p, const svh_arra
     SVH_TRY(validate(ctx, src, "img_source", SVH_F32, 2, 3));
     SVH_TRY(validate(ctx, tgt, "img_target", SVH_F32, 2, 3));
     if (!func_supported(p->match_func) || func_census(p->match_func))
-        return fail(ctx, SVH_ERR_UNSUPPORTED, "on-demand volumes take the float matching functions (CC ... ZSAD), not %d", p->match_func);
+        return fail(ctx, SVH_ERR_UNSUPPORTED, "on-demand volumes take the float matching functions (CC ... ZSAD), not %d (%s)", p->match_func, func_name(p->match_func));
     if (p->search_dims != 1 && p->search_dims != 2) return fail(ctx, SVH_ERR_INVALID_ARGUMENT, "search_dims must be 1 (stereo) or 2 (flow)");
     if (p->h_radius < 0 || p->v_radius < 0 || p->h_radius > 64 || p->v_radius > 64) return fail(ctx, SVH_ERR_INVALID_ARGUMENT, "bad window radius");
     if (src->ndim != tgt->ndim) return fail(ctx, SVH_ERR_INVALID_ARGUMENT, "image ranks differ");
@@ -1646,7 +1646,7 @@ extern "C" int svh_on_demand_features(svh_context *ctx, int match_func, const sv
     if (!ctx) return SVH_ERR_INVALID_ARGUMENT;
     SVH_TRY(validate(ctx, img, "img", SVH_F32, 2, 3));
     SVH_TRY(validate(ctx, out, "out", SVH_F32, 3, 3));
-    if (!func_supported(match_func) || func_census(match_func)) return fail(ctx, SVH_ERR_UNSUPPORTED, "matching function %d", match_func);
+    if (!func_supported(match_func) || func_census(match_func)) return func_refusal(ctx, match_func, "PatchMatch");
     if (h_radius < 0 || v_radius < 0 || h_radius > 64 || v_radius > 64) return fail(ctx, SVH_ERR_INVALID_ARGUMENT, "bad window radius");
     const int H = (int)img->shape[0], W = (int)img->shape[1], C = img->ndim == 3 ? (int)img->shape[2] : 1;
     const int nF = (2 * v_radius + 1) * (2 * h_radius + 1) * C;
@@ -1860,7 +1860,7 @@ extern "C" int svh_patch_match(svh_context *ctx, const svh_on_demand_params *par
     SVH_TRY(validate(ctx, feat_source, "feature_vol_s", SVH_F32, 3, 3));
     SVH_TRY(validate(ctx, feat_target, "feature_vol_t", SVH_F32, 3, 3));
     if (!func_supported(params->match_func) || func_census(params->match_func))
-        return fail(ctx, SVH_ERR_UNSUPPORTED, "PatchMatch takes the float matching functions (CC ... ZSAD), not %d", params->match_func);
+        return fail(ctx, SVH_ERR_UNSUPPORTED, "PatchMatch takes the float matching functions (CC ... ZSAD), not %d (%s)", params->match_func, func_name(params->match_func));
     if (params->search_dims != 1 && params->search_dims != 2) return fail(ctx, SVH_ERR_INVALID_ARGUMENT, "search_dims must be 1 (stereo) or 2 (flow)");
     if (feat_source->shape[2] != feat_target->shape[2]) return fail(ctx, SVH_EMPTY_RESULT, "feature counts differ"); // patchmatch.h:529-531
     if (params->search_dims == 1 && feat_source->shape[0] != feat_target->shape[0]) return fail(ctx, SVH_EMPTY_RESULT, "row counts differ"); // :533-537

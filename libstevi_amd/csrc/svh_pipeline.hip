@@ -19,7 +19,7 @@ extern "C" int svh_stereo_match(svh_context *ctx, const svh_stereo_params *prm, 
     SVH_TRY(validate_image(ctx, img_l, "img_l", prm->match_func));
     SVH_TRY(validate_image(ctx, img_r, "img_r", prm->match_func));
     const int func = prm->match_func;
-    if (!func_supported(func)) return fail(ctx, SVH_ERR_UNSUPPORTED, "matching function %d", func);
+    if (!func_volume_supported(func)) return fail(ctx, SVH_ERR_UNSUPPORTED, "matching function %d", func);
     if (prm->disp_direction != SVH_LEFT_TO_RIGHT && prm->disp_direction != SVH_RIGHT_TO_LEFT)
         return fail(ctx, SVH_ERR_INVALID_ARGUMENT, "bad disparity direction");
     if (prm->h_radius < 0 || prm->v_radius < 0 || prm->h_radius > 255 || prm->v_radius > 255)
@@ -46,6 +46,7 @@ extern "C" int svh_stereo_match(svh_context *ctx, const svh_stereo_params *prm, 
     const int D = prm->shard_count > 0 ? prm->shard_count : Dtot;
     if (sb < 0 || sb + D > Dtot) return fail(ctx, SVH_ERR_INVALID_ARGUMENT, "disparity shard outside [0, disp_count)");
     const bool sharded = D != Dtot;
+    if (sharded && func_median(func)) return func_refusal(ctx, func, "disparity shards");
     const int strategy = func_strategy(func);
     const bool sgm = prm->sgm_directions != 0;
     if (sharded && sgm)

@@ -22,6 +22,7 @@ template <typename TCV> struct OffsetedCostVolume { // hierarchical.h:33-37
 template <matchingFunctions matchFunc, typename T_L, typename T_R, dispDirection dDir = dispDirection::RightToLeft, typename TCV = float>
 OffsetedCostVolume<TCV> computeGuidedCV(Multidim::Array<T_L, 3> const &feature_vol_l, Multidim::Array<T_R, 3> const &feature_vol_r,
                                         Multidim::Array<disp_t, 2> disp_guide, disp_t upscale_disp_radius) {
+    static_assert(!HipBridge::wholeVolumeOnly<matchFunc>(), "libstevi_hip: MEDAD / ZMEDAD are taken by the whole-volume cost functions only, not by hierarchical matching");
     static_assert(HipBridge::onGpuPath<matchFunc>(), "libstevi_hip: this matching function has no GPU path");
     static_assert(std::is_same_v<TCV, float>, "libstevi_hip: cost volumes are float");
     auto l_shape = feature_vol_l.shape();
@@ -44,6 +45,7 @@ OffsetedCostVolume<TCV> hiearchicalTruncatedCostVolume(Multidim::Array<T_L, nImD
                                                        std::array<uint8_t, depth + 1> h_radiuses, std::array<uint8_t, depth + 1> v_radiuses,
                                                        disp_t disp_width, disp_t upscale_disp_radius = 2) {
     static_assert(depth > 0, "Minimum depth is 1"); // :243
+    static_assert(!HipBridge::wholeVolumeOnly<matchFunc>(), "libstevi_hip: MEDAD / ZMEDAD are taken by the whole-volume cost functions only, not by hierarchical matching");
     static_assert(HipBridge::onGpuPath<matchFunc>(), "libstevi_hip: this matching function has no GPU path");
     static_assert(std::is_same_v<TCV, float>, "libstevi_hip: cost volumes are float");
     auto l_shape = img_l.shape();

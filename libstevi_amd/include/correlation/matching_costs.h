@@ -8,11 +8,19 @@
 // index, no reassociation), so a vector compared here equals the same voxel of a GPU volume to the last bit for the integer functions
 // and within float rounding of the column-sum form for the others (tests/cpp/host_inlines.cpp).
 //
-// Not provided, by design: MEDAD / ZMEDAD / KERMI (no GPU path: onGpuPath<f>() is false and every entry point static_asserts on it),
-// and the barycentricBestApproximation members, which belong to image_based_refinement.h's feature-domain refinement (Eigen).
+// MedianAbsDiff (MEDAD / ZMEDAD, matching_costs.h:180-230) is here too, on the order the GPU uses: NaN ranks above +inf (NumPy's order;
+// the reference's nth_element on operator< has no defined result for NaN).  The differences are compared as their 31-bit keys
+// bits(fabs(d)) -- float order for every non-NaN value, every NaN above +inf --, so a vector compared here equals the same voxel of a GPU
+// volume bit for bit, NaN payload included.  MEDAD / ZMEDAD run on the whole-volume entry points only (featureVolume2CostVolume,
+// unfoldBasedCostVolume, unfoldBased2dDisparityCostVolume, getFeatureVolumeForMatchFunc, stereoMatch): hierarchical matching, PatchMatch
+// and the on-demand volumes refuse them at compile time (HipBridge::wholeVolumeOnly).
+//
+// Not provided, by design: KERMI (no GPU path: onGpuPath<f>() is false and every entry point static_asserts on it), and the
+// barycentricBestApproximation members, which belong to image_based_refinement.h's feature-domain refinement (Eigen).
 #ifndef STEREOVISION_MATCHING_COSTS_H
 #define STEREOVISION_MATCHING_COSTS_H
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -143,6 +151,40 @@ template <class T_S, class T_T> inline hamming_cv_t hammingDistance(std::vector<
     return score;
 }
 
+// MedianAbsDiff, matching_costs.h:180-230: the element of rank F/2 of |s_i - t_i| (the upper median for even F), differences formed in T_O
+namespace HipBridge {
+namespace detail {
+template <class T_O> inline bool medianLess(T_O a, T_O b) {
+    if constexpr (std::is_floating_point_v<T_O>) { // 31-bit keys: NaN above +inf (see the header comment)
+        static_assert(sizeof(T_O) == sizeof(uint32_t), "libstevi_hip: MedianAbsDiff forms its differences in float");
+        return (bitsOf(a) & 0x7fffffffu) < (bitsOf(b) & 0x7fffffffu);
+    } else {
+        return a < b;
+    }
+}
+template <class T_S, class T_T, class T_O, class VS, class VT> inline T_O medianAbs(VS const &source, VT const &target) {
+    checkOutputType<T_S, T_T, T_O>();
+    const int n = length(source);
+    std::vector<T_O> diffs(static_cast<std::size_t>(n));
+    for (int i = 0; i < n; i++) {
+        const T_O tmp = T_O(element(source, i)) - T_O(element(target, i));
+        if constexpr (std::is_integral_v<T_O>) diffs[i] = static_cast<T_O>(std::abs(tmp));
+        else diffs[i] = std::fabs(tmp);
+    }
+    const int medianPos = n / 2;
+    std::nth_element(diffs.begin(), diffs.begin() + medianPos, diffs.end(), medianLess<T_O>);
+    return diffs[static_cast<std::size_t>(medianPos)];
+}
+} // namespace detail
+} // namespace HipBridge
+template <class T_S, class T_T, class T_O = float, Multidim::ArrayDataAccessConstness viewConstness = Multidim::ConstView>
+inline T_O MedianAbsDiff(Multidim::Array<T_S, 1, viewConstness> const &source, Multidim::Array<T_T, 1, viewConstness> const &target) {
+    return HipBridge::detail::medianAbs<T_S, T_T, T_O>(source, target);
+}
+template <class T_S, class T_T, class T_O = float> inline T_O MedianAbsDiff(std::vector<T_S> const &source, std::vector<T_T> const &target) {
+    return HipBridge::detail::medianAbs<T_S, T_T, T_O>(source, target);
+}
+
 template <matchingFunctions func> class MatchingFunctionTraits {};
 
 // One traits class per function (matching_costs.h:419-685): the constants, and featureComparison = the vector comparison above that
@@ -165,6 +207,7 @@ template <matchingFunctions func> class MatchingFunctionTraits {};
 #define SVH_SSD (SumSquareDiff<T_S, T_T, T_O>(source, target))
 #define SVH_SAD (SumAbsDiff<T_S, T_T, T_O>(source, target))
 #define SVH_HAM (hammingDistance(source, target))
+#define SVH_MEDAD (MedianAbsDiff<T_S, T_T, T_O>(source, target))
 SVH_MATCH_TRAITS(NCC, "NCC", false, true, Score, false, T_O, SVH_DOT)
 SVH_MATCH_TRAITS(CC, "CC", false, false, Score, false, float, SVH_DOT)
 SVH_MATCH_TRAITS(SSD, "SSD", false, false, Cost, false, float, SVH_SSD)
@@ -173,12 +216,15 @@ SVH_MATCH_TRAITS(ZCC, "ZCC", true, false, Score, false, float, SVH_DOT)
 SVH_MATCH_TRAITS(ZNCC, "ZNCC", true, true, Score, false, float, SVH_DOT)
 SVH_MATCH_TRAITS(ZSSD, "ZSSD", true, false, Cost, false, float, SVH_SSD)
 SVH_MATCH_TRAITS(ZSAD, "ZSAD", true, false, Cost, false, float, SVH_SAD)
+SVH_MATCH_TRAITS(MEDAD, "MEDAD", false, false, Cost, false, float, SVH_MEDAD)
+SVH_MATCH_TRAITS(ZMEDAD, "ZMEDAD", true, false, Cost, false, float, SVH_MEDAD)
 SVH_MATCH_TRAITS(HAMMING, "HAMMING", false, false, Cost, true, float, SVH_HAM)
 SVH_MATCH_TRAITS(CENSUS, "CENSUS", false, false, Cost, true, float, SVH_HAM)
 #undef SVH_DOT
 #undef SVH_SSD
 #undef SVH_SAD
 #undef SVH_HAM
+#undef SVH_MEDAD
 #undef SVH_MATCH_TRAITS
 
 // defaultCvValForMatchFunc / optimalDispAndCost, matching_costs.h:687-723: the neutral starting value of a search and one step of it
@@ -213,8 +259,11 @@ namespace HipBridge {
 template <matchingFunctions f> constexpr bool onGpuPath() {
     return f == matchingFunctions::CC || f == matchingFunctions::NCC || f == matchingFunctions::SSD || f == matchingFunctions::SAD ||
            f == matchingFunctions::ZCC || f == matchingFunctions::ZNCC || f == matchingFunctions::ZSSD || f == matchingFunctions::ZSAD ||
-           f == matchingFunctions::HAMMING || f == matchingFunctions::CENSUS;
+           f == matchingFunctions::MEDAD || f == matchingFunctions::ZMEDAD || f == matchingFunctions::HAMMING || f == matchingFunctions::CENSUS;
 }
+// functions taken by the whole-volume entry points only (cross_correlations.h, stereoMatch): hierarchical matching, PatchMatch and the
+// on-demand volumes static_assert on it
+template <matchingFunctions f> constexpr bool wholeVolumeOnly() { return f == matchingFunctions::MEDAD || f == matchingFunctions::ZMEDAD; }
 } // namespace HipBridge
 
 } // namespace Correlation

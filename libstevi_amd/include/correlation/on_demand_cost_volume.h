@@ -79,6 +79,7 @@ template <matchingFunctions matchFunc, class T_CV, class F_V_S_T, class F_V_T_T,
     static constexpr int nDim = SearchSpaceType::nDim;
     static constexpr int nSearchDim = SearchSpaceType::nDimsOfType(SearchSpaceBase::Search);
     static constexpr int nCostVolDim = nDim + nSearchDim - 1;
+    static_assert(!HipBridge::wholeVolumeOnly<matchFunc>(), "libstevi_hip: MEDAD / ZMEDAD are taken by the whole-volume cost functions only, not by the on-demand volumes");
     static_assert(nDim == 3 && (nSearchDim == 1 || nSearchDim == 2), "libstevi_hip: stereo (IgnoredDim, SearchDim, FeatureDim) or flow (SearchDim, SearchDim, FeatureDim)");
     static_assert(HipBridge::OnDemandSupport<matchFunc, F_V_S_T>::value && HipBridge::OnDemandSupport<matchFunc, F_V_T_T>::value,
                   "libstevi_hip: on-demand volumes are evaluated for float images decorated with ZNFeaturesVolumeDecorator<ZeroMean, Normalized> of the matching function");

@@ -60,6 +60,7 @@ template <matchingFunctions matchFunc, int searchSpaceDim, class T_FV_S, class T
 Multidim::Array<disp_t, 3> cachelessPatchMatch(T_FV_S const &f_s_p, T_FV_T const &f_t_p, searchOffset<searchSpaceDim> searchOffset, int nIter = 5,
                                                int nRandomSearch = 4, InitializerT initializer = std::nullopt, RandCacheT = std::nullopt) {
     static_assert(searchSpaceDim == 1 or searchSpaceDim == 2, "patchMatch function can only be used to search in 1 or two dimension !");
+    static_assert(!HipBridge::wholeVolumeOnly<matchFunc>(), "libstevi_hip: MEDAD / ZMEDAD are taken by the whole-volume cost functions only, not by PatchMatch");
     static_assert(HipBridge::OnDemandSupport<matchFunc, T_FV_S>::value && HipBridge::OnDemandSupport<matchFunc, T_FV_T>::value,
                   "libstevi_hip: PatchMatch runs on float images decorated with ZNFeaturesVolumeDecorator<ZeroMean, Normalized> of the matching function");
     Multidim::Array<disp_t, 3> disp;
@@ -89,6 +90,7 @@ Multidim::Array<disp_t, 3> patchMatch(Multidim::Array<T_S, 3, C_S> const &featur
                                       searchOffset<searchSpaceDim> searchOffset, int nIter = 5, int nRandomSearch = 4, InitializerT initializer = std::nullopt,
                                       RandCacheT = std::nullopt) {
     static_assert(searchSpaceDim == 1 or searchSpaceDim == 2, "patchMatch function can only be used to search in 1 or two dimension !");
+    static_assert(!HipBridge::wholeVolumeOnly<matchFunc>(), "libstevi_hip: MEDAD / ZMEDAD are taken by the whole-volume cost functions only, not by PatchMatch");
     static_assert(std::is_same_v<std::remove_const_t<T_S>, float> && std::is_same_v<std::remove_const_t<T_T>, float>,
                   "libstevi_hip: PatchMatch takes float feature volumes");
     static_assert(!MatchingFunctionTraits<matchFunc>::isCensusBased && HipBridge::onGpuPath<matchFunc>(), "libstevi_hip: PatchMatch takes the float matching functions (CC ... ZSAD)");
