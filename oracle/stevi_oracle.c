@@ -6,16 +6,17 @@
  * as the checker / the CPU baseline.  The HIP library (libstevi_amd/csrc) never links it.
  *
  * PARITY STATUS (see DESIGN.md "Oracle"):
- *   - the reference cannot be built in this image (MultidimArrays, StatusOptional, Eigen, FFTW
- *     are absent; CMakeLists.txt:62-76,:92,:95) and its tests hold no golden vectors (all inputs
- *     come from std::random_device, test/unittests/testCorrelationFilters.cpp:76-79);
+ *   - the reference library as a whole cannot be built (MultidimArrays, StatusOptional, Eigen,
+ *     FFTW are absent; CMakeLists.txt:62-76,:92,:95) and its tests hold no golden vectors (all
+ *     inputs come from std::random_device, test/unittests/testCorrelationFilters.cpp:76-79);
  *   - rows pinned by the reference's own property tests, restated in tests/test_oracle_pins.py:
  *     unfold (testCorrelationFilters.cpp:384-445), ZCC/ZNCC volumes (:264-370,:462-500),
  *     NCC/SSD/ZSSD/SAD/ZSAD arithmetic (testCorrelation2d.cpp:75-127 via
  *     test/test_correlation_utils.h:9-310), parabola refinement (testCostRefinement.cpp:33-57);
- *   - rows with NO reference test or fixture -- census, Hamming, SGM, extractSelectedIndex tie
- *     rule, truncatedCostVolume: **parity unpinned**; they follow the cited lines operation by
- *     operation and are cross-checked only against hand-computed cases.
+ *   - rows with no reference test or fixture -- census, Hamming, SGM, extractSelectedIndex tie
+ *     rule, truncatedCostVolume, the equiangular / Gaussian kernels: pinned against the
+ *     reference's own headers, compiled unchanged into oracle/_ref/libstevi_refpin.so by
+ *     oracle/ref_pin.cpp (tests/test_reference_pins.py), besides hand-computed cases.
  *
  * All arrays are dense, row-major, last index fastest:
  *   images  [H][W][C]      feature volumes [H][W][F]      census words [H][W][nW]

@@ -3,9 +3,10 @@
 The reference has no golden vectors: every unit test draws inputs from std::random_device and
 compares against a naive in-test formula or an analytic value.  Each test below restates one of
 those tests on seeded inputs, so the oracle rows A1, A5-A8 and A12 are pinned the same way the
-reference pins itself.  Census, Hamming, SGM, the argmin tie rule and the truncated volume have
-no reference test ("parity unpinned", see oracle/stevi_oracle.c) and are covered by
-tests/test_oracle_semantics.py against hand-computed cases only.
+reference pins itself.  Census, Hamming, SGM, the argmin tie rule, the truncated volume and the
+equiangular / Gaussian kernels have no reference test; they are pinned against the reference's own
+code, compiled by build() into oracle/_ref/libstevi_refpin.so (tests/test_reference_pins.py), and
+against hand-computed cases in tests/test_oracle_semantics.py.
 """
 import numpy as np
 import pytest
